@@ -10,6 +10,11 @@ gloo on CPU tensors carries only the barrier and the max-over-ranks time.
     python bench.py [--gpus N] [--steps K] [--warmup W] [--suite aes128gcm|aes256gcm|chacha20poly1305]
                     [--packets N | --total-packets T] [--pt BYTES] [--keys K]
                     [--mode device|e2e|rx|keys|txq|packet] [--rotate] [--pipe CHUNK_PKTS,CHUNK_MIB,SLOTS]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line.  --full adds what takes runs of its
+own beside the timed steps (device mode: the CPU baseline leg).  --dump-outputs DIR writes what the last timed step
+left for its caller (device mode) as DIR/<name>.npy; the inputs are seeded, so two builds compare output for output.
 
 BASELINE configs[4] (C5, key-update churn end to end, strong split):
     python bench.py --mode e2e --keys 4096 --rotate --total-packets 16777216
@@ -171,6 +176,28 @@ def cpu_baseline(suite, pt, aad, seconds):
     }
 
 
+DUMP_SAMPLE_PACKETS = 8192  # packets of the arena kept by --dump-outputs
+DUMP_SAMPLE_BYTES = 40e6  # ... and the float32 bytes they may take (the whole dump stays under 64 MB)
+DUMP_STATUS_BYTES = 16e6  # every packet's status is kept while it fits in this, else the sampled packets' only
+
+
+def dump_outputs(path, n, stride, d_arena, d_mask, d_status, hp):
+    """--dump-outputs (device mode): what the last timed step left for its caller, as float32 .npy files.  The arena
+    is too large to keep whole, so a fixed, seeded sample of packets is kept: their arena rows after the open
+    ([AAD | plaintext | the seal's tag], which depends on every ciphertext byte), the 5-byte HP masks of the seal and
+    the open's status; `packet_index` names the sampled packets."""
+    os.makedirs(path, exist_ok=True)
+    k = max(1, min(n, DUMP_SAMPLE_PACKETS, int(DUMP_SAMPLE_BYTES // (4 * stride))))
+    idx = np.sort(np.random.default_rng(0x5eed0d00).choice(n, k, replace=False))
+    rows = np.stack([d_arena.download(stride, offset=int(i) * stride) for i in idx])
+    st = d_status.download(dtype=np.int8)
+    np.save(os.path.join(path, "packet_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(path, "packets.npy"), rows.astype(np.float32))
+    np.save(os.path.join(path, "status.npy"), (st if 4 * n <= DUMP_STATUS_BYTES else st[idx]).astype(np.float32))
+    if hp:
+        np.save(os.path.join(path, "hp_masks.npy"), d_mask.download().reshape(n, 5)[idx].astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -203,12 +230,19 @@ def main():
     ap.add_argument("--coalesce", type=int, default=1, help="txq: bursts sent per launch (qpp_txq_set_coalesce)")
     ap.add_argument("--txq-launch", action="store_true",
                     help="txq --inflight 1: the launched path (qpp_txq_create) instead of the persistent server")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what is measured beside the timed steps (device mode: the CPU baseline leg)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="device mode: after the timed steps, write what the last step left for its caller (a seeded "
+                         "sample of the arena's packets, their HP masks, the statuses) as DIR/<name>.npy, float32")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline leg")
     ap.add_argument("--no-hp", action="store_true", help="seal without the HP mask (diagnostic)")
     ap.add_argument("--no-check", action="store_true", help="skip the warmup open-status check (diagnostic builds)")
     ap.add_argument("--no-server", action="store_true", help="--mode packet: one launch per call (no packet server)")
     args = ap.parse_args()
 
+    if args.dump_outputs and args.mode != "device":
+        raise SystemExit("--dump-outputs: device mode only")
     rank, world, local_rank = multigpu.env_rank()
     if args.total_packets:  # strong split: rank r owns [r*T/w, (r+1)*T/w)
         lo, hi = args.total_packets * rank // world, args.total_packets * (rank + 1) // world
@@ -291,6 +325,8 @@ def main():
     seal_ms = [ctx.elapsed_ms(a, b) for a, b, _ in evs]
     open_ms = [ctx.elapsed_ms(b, c) for _, b, c in evs]
     t_max = max_over_ranks(t_ms)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, n, d_arena.nbytes // n, d_arena, d_mask, d_status, not args.no_hp)
 
     payload = 2.0 * (args.total_packets or n * world) * pt * args.steps  # seal + open, all ranks
     # HBM bytes per seal launch from the committed PMC profile of this workload (tools/profile.sh + tools/traffic.py);
@@ -362,7 +398,7 @@ def main():
                          "model": "bench.aes_valu_per_packet, calibrated on SQ_INSTS_VALU; peak measured by "
                                   "tools/ubench/issue.hip"},
             }
-        if world == 1 and not args.no_cpu and suite:
+        if args.full and world == 1 and not args.no_cpu and suite:
             out["cpu_baseline"] = cpu_baseline(suite, pt, aad, args.cpu_seconds)
         print(json.dumps(out), flush=True)
     ctx.close()
