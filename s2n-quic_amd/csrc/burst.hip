@@ -428,7 +428,7 @@ __global__ __launch_bounds__(kBurstWG) void aes_gcm_burst_kernel(const DevKey *_
 //   done = seq; the host waits for all of them;
 // * a workgroup leaves on the stop word, or after idle_ticks without a flush -- the host never posts to a server
 //   that may be leaving on its own: after a quarter of that idle time without a post it stops the server and starts
-//   a new one first (api.cpp srv_submit), so a flush is seen by every workgroup or by none (the idle exit is for a
+//   a new one first (txq.cpp srv_submit), so a flush is seen by every workgroup or by none (the idle exit is for a
 //   host that went away).
 
 // A transmit flush's packet is sealed and header-protected; a per-packet request (kTxsPktNoHp: Key::encrypt,
@@ -602,7 +602,7 @@ __device__ __forceinline__ void txs_two_wave(const AesLds &aes, const qpp_pkt &d
 
 // one 16-byte chunk of the slot (lane < kTxsPollLanes), in ONE load past every cache (sc0 sc1: the host writes it;
 // a chunk is read whole, so its tag vouches for its other words)
-// lane kTxsPollLanes reads the device's eviction word in the same load (api.cpp release: every resident server of the
+// lane kTxsPollLanes reads the device's eviction word in the same load (servers.cpp release: every resident server of the
 // device leaves at its next poll without a complete flush, so that a free past the parked bound need not wait for it)
 __device__ __forceinline__ uint4 txs_poll(const TxsSlot *slot, const uint32_t *evict, uint32_t lane) {
     typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));

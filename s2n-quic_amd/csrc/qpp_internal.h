@@ -1,4 +1,4 @@
-// qpp_internal.h — shared between the host runtime (api.cpp, kdf.cpp) and the HIP kernels.
+// qpp_internal.h — shared between the host runtime (host.h and its units, kdf.cpp) and the HIP kernels.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -158,15 +158,15 @@ uint32_t burst_packets_per_item(uint32_t n, uint32_t n_cu);
 hipError_t launch_aes_gcm_burst(bool seal, const DevKey *keys, const qpp_pkt *descs, const PlanBuffers &pb,
                                 uint32_t n, uint32_t key_cap, uint32_t per, uint8_t *arena, uint8_t *masks,
                                 int8_t *status, uint32_t flags, uint32_t suites, const PowTables &pow, hipStream_t s);
-// Persistent transmit-queue server (burst.hip txq_server_kernel; api.cpp qpp_txq_create_persistent).
+// Persistent transmit-queue server (burst.hip txq_server_kernel; txq.cpp qpp_txq_create_persistent).
 // One TxsSlot per server workgroup in pinned, coherent host memory: the host writes the workgroup's first work item
 // and its descriptors (each tagged with the flush's seq) and then seq; the workgroup polls its slot (one wave-wide
 // read gets the flush, the item and the descriptors together) and writes `done` = seq when its packets are sealed.
 constexpr uint32_t kTxsWaves = 8;  // server workgroup = 8 waves, one packet per wave per work item
 constexpr uint32_t kTxsItemsMask = 0xffffffu;
 constexpr uint32_t kTxsStop = 0xffffffu;
-// Descriptor flags of the per-packet requests (qpp_seal / qpp_open through the context's packet server, api.cpp
-// run_one_server): never set by the transport (qpp_txq_push_descs refuses any flag)
+// Descriptor flags of the per-packet requests (qpp_seal / qpp_open through the context's packet server, packet.cpp
+// packet_server_run): never set by the transport (qpp_txq_push_descs refuses any flag)
 constexpr uint8_t kTxsPktNoHp = 0x40;  // seal without header protection (Key::encrypt), status written
 constexpr uint8_t kTxsPktOpen = 0x80;  // open (Key::decrypt), status written
 constexpr uint32_t kTxsMaskNr = 0xffu;  // WorkItem.nr of a header-protection mask item (qpp_hp_mask, qpp_header_key_mask)

@@ -358,7 +358,7 @@ def test_host_pipeline(ctx, ops):
 @pytest.mark.parametrize("suite", [1, 2])
 def test_single_live_key_batches_run_without_a_plan(suite):
     """With exactly one live packet key (an AES one) the quad kernel runs without the plan launches
-    (api.cpp single_aes_slot); packets naming any other slot are still refused with INTERNAL_ERROR and left untouched,
+    (batch.cpp single_aes_slot); packets naming any other slot are still refused with INTERNAL_ERROR and left untouched,
     the rest are bit-exact, and open round-trips."""
     c = qpp.Context(0)
     try:

@@ -1,5 +1,5 @@
 """Per-packet Key::encrypt / Key::decrypt (crypto/src/cipher_suite.rs:86-160, the packet_protection.rs trait face)
-through the context's packet server (api.cpp packet_server_run; burst.hip txq_server_kernel, kTxsPktNoHp /
+through the context's packet server (packet.cpp packet_server_run; burst.hip txq_server_kernel, kTxsPktNoHp /
 kTxsPktOpen items): bit-exact against the oracle and against the launched path, for every suite, header and payload
 lengths from empty to the server's 16 KiB ring, tampered tags, keys spread over the server's workgroups, the server
 stopped and restarted between calls, FIPS seals and long packets on the launched path."""
@@ -113,7 +113,7 @@ def test_server_restarts_and_long_packets(monkeypatch):
 def test_device_free_keeps_the_server(monkeypatch):
     """device and pinned frees leave the packet server resident (one launch for every call): hipFree / hipHostFree
     would wait for it, so a buffer freed while a server of the device is resident is parked and freed by the next
-    synchronize that finds none (api.cpp release)"""
+    synchronize that finds none (servers.cpp release)"""
     monkeypatch.setenv("QPP_TXQ_SERVER_IDLE_MS", "10000")
     rng = np.random.default_rng(7301)
     ctx = qpp.Context(0)

@@ -3,7 +3,7 @@
 The reference's keys are independent `Send` objects any endpoint task may own (quic/s2n-quic-core/src/crypto/key.rs:8),
 and one endpoint event loop drives receive and transmit together (quic/s2n-quic-core/src/io/event_loop.rs:39-165).  So
 several contexts of one process -- each with its own packet server (qpp_seal / qpp_open / qpp_hp_mask) and maybe a
-persistent transmit queue -- share the GPU while fused receives run.  api.cpp's device registry (DevServers) keeps:
+persistent transmit queue -- share the GPU while fused receives run.  servers.cpp's device registry (DevServers) keeps:
   * the fused receive's grid sized for the CUs every context's resident servers leave (its grid barriers need every
     workgroup resident), fused receives of the device one after another, and a server launch behind the latest fused
     receive (a server starting while the receive's workgroups are dispatched would take CUs its grid counted on);

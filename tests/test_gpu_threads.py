@@ -3,8 +3,8 @@
 The reference's keys are `Send` objects that any endpoint task may own (quic/s2n-quic-core/src/crypto/key.rs:8), and
 a server process runs one endpoint event loop per thread (quic/s2n-quic-core/src/io/event_loop.rs:39-165): so several
 contexts of one process call the library concurrently.  ctypes releases the GIL for every library call, so the three
-threads below really overlap inside api.cpp: per-packet seals through a packet server with device and pinned frees in
-between (the parked-free path, api.cpp release), persistent transmit-queue flushes with key-table growth (a server
+threads below really overlap inside the host runtime: per-packet seals through a packet server with device and pinned
+frees in between (the parked-free path, servers.cpp release), persistent transmit-queue flushes with key-table growth (a server
 stop, a table move, the old table released), and 64-key fused receives with context synchronizes (the device
 registry's lock: receive grids, server slots, server starts behind the latest receive).
 Bar: every byte bit-exact, no receive barrier timeout, no thread stuck (each finishes within its budget).

@@ -1,7 +1,7 @@
 """Transmit-queue ordering rules with several flushes in flight, on the GPU.
 
 * FIPS nonce order across streams: the gate state lives in the device key record, so the gates of two flushes that
-  are in flight on different streams must run in submission order (api.cpp fips_gate: one context-wide event).  A pn
+  are in flight on different streams must run in submission order (batch.cpp fips_gate: one context-wide event).  A pn
   repeated across two such flushes is refused in the second, exactly as the sequential rule (aws-lc's TLS 1.3 sealer,
   quic/s2n-quic-crypto/src/aead/fips.rs:13-60) refuses it -- parity against orc_fips_seal_ok.
 * DMA path ownership: a flush copies only its own packets' bytes to HBM and back (runs of adjacent packets), never the

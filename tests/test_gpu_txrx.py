@@ -174,7 +174,7 @@ def test_tx_and_rx_with_resident_server(monkeypatch):
 
 def test_frees_with_resident_server_return_quickly(monkeypatch):
     """hipFree waits for every stream of the device, a resident server's too: a free (and a plan growth, which frees
-    the old plan) while a persistent queue is live is parked instead (api.cpp release) -- the call returns in
+    the old plan) while a persistent queue is live is parked instead (servers.cpp release) -- the call returns in
     milliseconds, not after the server's idle time, and the server stays resident for the next flushes, bit-exact"""
     monkeypatch.setenv("QPP_TXQ_SERVER_IDLE_MS", "30000")
     rng = np.random.default_rng(4041)

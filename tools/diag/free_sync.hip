@@ -1,7 +1,7 @@
 // free_sync.hip — which HIP free calls wait for a resident (persistent) kernel on ANOTHER stream?
 //
-// api.cpp stops a context's resident servers before every hipFree / hipHostFree (quiet_for_free), because those calls
-// wait for every stream of the device.  With several contexts per process, one context's free would also wait for
+// The host runtime used to stop a context's resident servers before every hipFree / hipHostFree, because those calls
+// wait for every stream of the device (what it does now: ctx.cpp, "Memory without device-wide waits").  With several contexts per process, one context's free would also wait for
 // another context's server, which leaves only when idle.  This program measures each free form beside a bounded
 // resident kernel (it spins on a host-mapped stop word and exits by itself after 2 s at the latest):
 //   hipFree, hipHostFree, hipFreeAsync (memory from hipMallocAsync) + hipStreamSynchronize of its own stream,
