@@ -528,11 +528,11 @@ struct CtrPageQ4 {
 #ifndef QPP_Q4_DEPTH
 #define QPP_Q4_DEPTH 3  // units (4 lookups each) issued ahead of the one combined (<= NB - 1)
 #endif
-template <int NR, int NB, int STRIDE = 1>
+template <int NR, int NB, int STRIDE = 1, int DEPTH = QPP_Q4_DEPTH>
 __device__ __forceinline__ void ctr_keystream_q4(const AesQ4 &a, const CtrPageQ4 &pg, const uint32_t *__restrict__ rk,
                                                  uint32_t c0, uint4 (&ks)[NB]) {
     static_assert(NB >= 1 && NB <= 4, "pipeline depth NB - 1 lookups groups of 4 within the 15-read counter");
-    constexpr int D = NB - 1 < QPP_Q4_DEPTH ? NB - 1 : QPP_Q4_DEPTH;
+    constexpr int D = NB - 1 < DEPTH ? NB - 1 : DEPTH;
     constexpr int U = (NR - 2) * 4 * NB;  // units of rounds 3..NR
     uint32_t st[NB][4];
     uint32_t nw[4];

@@ -23,7 +23,9 @@ namespace dev {
 #ifndef QPP_GHASH_DEPTH
 #define QPP_GHASH_DEPTH 9  // LDS reads in flight per GHASH product (PIPE)
 #endif
-template <bool PIPE>
+// (DEPTH: the reads in flight of this instance, 9 or a multiple of 3 -- a kernel with more waves per SIMD and fewer
+// registers takes fewer, quad.hip; ACC: the running-sum form prod_acc, DEPTH even)
+template <bool PIPE, int DEPTH = QPP_GHASH_DEPTH, bool ACC = false>
 struct GhashT {
     uint32_t lc[4];   // byte i of lc[k] = 16 * j(k, i)
     uint32_t sel[4];  // v_perm selector of step i: byte0 <- lc[k].b_i, byte1 <- W[k].b_((i+b)&3), bytes 2,3 <- 0
@@ -71,7 +73,8 @@ struct GhashT {
             const uint4 h = xor3(e, f, look<3, 3>(w));
             return xor3(g, h, c);
         }
-        if constexpr (QPP_GHASH_DEPTH != 9) return prod_d<QPP_GHASH_DEPTH>(w, c);
+        if constexpr (ACC) return prod_acc<DEPTH>(w, c);
+        if constexpr (DEPTH != 9) return prod_d<DEPTH>(w, c);
         uint4 l[16];
         auto issue = [&](auto ic) {
             constexpr int i = decltype(ic)::value;
@@ -117,6 +120,28 @@ struct GhashT {
         });
         __builtin_amdgcn_sched_barrier(0);
         return xor3(xor3(x[0], x[1], x[2]), xor3(x[3], x[4], l[15]), c);
+    }
+    // D reads in flight (D even), summed into one running value two at a time: the same 8 xor3 per word as the trees
+    // above, but 4 + 4 D live registers instead of the 20 + 4 D of prod_d's partial sums (the 128-VGPR instances)
+    template <int D>
+    __device__ __forceinline__ uint4 prod_acc(const uint4 &w, uint4 c) const {
+        static_assert(D % 2 == 0 && D >= 2 && D <= 16, "reads are consumed in pairs");
+        uint4 l[16];
+        auto issue = [&](auto ic) {
+            constexpr int i = decltype(ic)::value;
+            if constexpr (i < 16) l[i] = look<i / 4, i % 4>(w);
+        };
+        static_for<D>(issue);
+        uint4 acc = c;
+        static_for<8>([&](auto tc) {
+            constexpr int t = decltype(tc)::value;
+            __builtin_amdgcn_sched_barrier(0);
+            acc = xor3(acc, l[2 * t], l[2 * t + 1]);
+            issue(std::integral_constant<int, 2 * t + D>{});
+            issue(std::integral_constant<int, 2 * t + D + 1>{});
+        });
+        __builtin_amdgcn_sched_barrier(0);
+        return acc;
     }
     // one chain step: W' = rot(Z * H ^ c)
     __device__ __forceinline__ uint4 mulx(const uint4 &w, uint4 c) const { return rot(prod(w, c)); }

@@ -220,7 +220,8 @@ hipError_t launch_aes_gcm(bool seal, const DevKey *keys, const qpp_pkt *descs, c
 hipError_t launch_aes_gcm_single(bool seal, const DevKey *keys, const qpp_pkt *descs, uint32_t slot, uint32_t nr,
                                  uint32_t n, uint32_t n_cu, uint8_t *arena, uint8_t *masks, int8_t *status,
                                  uint32_t flags, const PowTables &pow, hipStream_t s);
-// quad.hip: the quad-layout (4 lanes per packet, 768-thread workgroups) throughput kernel behind the two above
+// quad.hip: the quad-layout (4 lanes per packet; 768-thread workgroups, 1024 in the AES-128-only pair) throughput kernel
+// behind the two above
 // quad.hip: fused unprotect -> PN expand -> key-phase choice -> open for any mix of live packet keys (AES-128 and
 // AES-256 opened in the launch -- aes = 10 / 14 when only one size is live, 0 for both; ChaCha20 packets, when `chacha`, sorted to perm[scratch[3], + scratch[2]) for
 // launch_chacha_sel behind it), one cooperative launch of `grid` workgroups (<= the CUs it may use; key_cap <=

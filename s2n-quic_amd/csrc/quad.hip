@@ -11,7 +11,8 @@
 // payload staging (32 KiB of LDS next to 128 KiB of tables) and its ~220 VGPRs.  Here the 4 lanes of a quad move a
 // packet's bytes themselves -- lane s takes counter slots t = 4 k + s, so each wave instruction loads 64 contiguous
 // bytes of each of 16 packets and one 4-block group of a lane covers 256 contiguous bytes of its packet -- with no
-// staging at all; a workgroup is 768 threads (12 waves, 3 per SIMD, <= 168 VGPRs: QPP_QUAD_WG).
+// staging at all; a workgroup is 768 threads (12 waves, 3 per SIMD, <= 168 VGPRs) -- 1024 threads (16 waves, 4 per SIMD,
+// <= 128 VGPRs) in the AES-128-only seal / open pair: the geometry constants below.
 //
 // GHASH over four lanes: the sequence X_1..X_n (AAD blocks, ciphertext blocks, length block) is dealt to the lanes
 // by virtual slot (AAD block i at t = i + 1 - a, ciphertext block j at t = j + 1, length block at t = m + 1; lane
@@ -35,11 +36,34 @@ using namespace dev;
 
 constexpr uint32_t kQLdsPow = 131072;  // 4-bit tables of H^1..H^4
 constexpr uint32_t kQLdsVe = 65536;    // V_e during the build
+// Workgroup geometry, one constant per kernel family (launch bounds, quad_slices' pass width and the host launch all
+// read kQuadWG<NR> / kRxWG<AES>):
+//   QPP_QUAD_WG128  the AES-128-only seal / open pair (aes_gcm_quad_kernel<*, 10>: the HEAD instances, the headline)
+//   QPP_QUAD_WG     the both-sizes instances (<*, 0>) and the fused receive kernel's AES-128 / both-sizes instances
+//   QPP_QUAD_WG256  the AES-256-only instances (60 round-key words, 14 rounds of pipeline state)
+// 768 = 12 waves, 3 per SIMD, <= 168 VGPRs, 192 packets per pass; 1024 = 16 waves, 4 per SIMD, <= 128 VGPRs, 256 per pass
+// (a workgroup's 4096-packet slice of a 1 Mi batch on 256 CUs is 16 passes, not 21.33).
+// The AES-128 pair at 1024 threads fits 128 VGPRs with 32 B/lane of scratch (the ceiling csrc/check_resources.py holds
+// it to, with the occupancy), no scratch access in any keystream or product block and none in the group loop; what is
+// left runs once per packet or rarer (in the seal one reload of 16 (s - 1) in the first and the last group's address
+// arithmetic).  QuadCfg below: 6 GHASH reads in flight summed into one running value, group 0 peeled off the group
+// loop, the general path's slot number laundered (profiles/wg1024/isa_report.txt).  Measured against the 768-thread build, one box, alternating
+// rounds of the 20-step bench, 7 rounds (profiles/wg1024/ab.txt): 1 Mi x 1200 B, 1 key 2.1841 / 2.1886 (the 768 build
+// twice: the noise floor, 0.2 %) -> 2.1592 ms per step, -1.2 % (seal 1.1056 -> 1.0952, open 1.0745 -> 1.0570 ms);
+// 1 Mi x 300 B 0.7481 / 0.7476 -> 0.7278 ms, -2.7 %.  LDS-array busy 0.71 -> 0.74 (seal), 0.72 -> 0.76 (open), VALU 0.67
+// -> 0.69 / 0.66 -> 0.69 (profiles/wg1024/).  Earlier trials of 1024 threads spilled in the group loop: 9 % slower
+// (round 3, 37-44 VGPRs spilled), a tie (round 5, 16-30 spilled).  Deeper or shallower pipelines at 1024 threads, same
+// box, 5 rounds (ms per step): 8 reads in flight 2.2498, 4 reads 2.2161, prod_d's partial sums 2.2407, QPP_Q4_DEPTH 2
+// 2.2274, against 2.2144 as built and 2.2610 at 768.  The cost: the seal's HBM traffic rose 10 % in reads and 5 % in
+// writes (FETCH_SIZE / WRITE_SIZE, same box: sixteen waves' streams through one L2 instead of twelve).
+#ifndef QPP_QUAD_WG128
+#define QPP_QUAD_WG128 1024
+#endif
 #ifndef QPP_QUAD_WG
-#define QPP_QUAD_WG 768  // AES-128: 3 waves per SIMD (<= 168 VGPRs); 1024 (4 waves, <= 128) spills, 9 % slower (r03w4)
+#define QPP_QUAD_WG 768
 #endif
 #ifndef QPP_QUAD_WG256
-#define QPP_QUAD_WG256 768  // AES-256 (60 round-key words, 14 rounds of pipeline state)
+#define QPP_QUAD_WG256 768
 #endif
 // AES on four quarter-split T-tables (AesQ4, device_common.h; the two-table AesLds + rotl16 form measured 2 % slower
 // in the quad kernel, round 4, profiles/r04a)
@@ -47,7 +71,7 @@ using QAes = AesQ4;
 using QPage = CtrPageQ4;
 __device__ __forceinline__ QAes make_qaes() { return AesQ4::make(); }
 __device__ __forceinline__ void build_qaes() { build_aes_tables_q4(kLdsAes); }
-template <int NR, int NB, int STRIDE>
+template <int NR, int NB, int STRIDE, int DEPTH>
 __device__ __forceinline__ void qkeystream(const QAes &a, const QPage &pg, RkPtr rkp, uint32_t c0,
                                            uint4 (&ks)[NB]) {
     // rounds 3..NR only: 32 / 48 words at the group's start (the page build reads rounds 0..2 itself, when it runs)
@@ -57,7 +81,7 @@ __device__ __forceinline__ void qkeystream(const QAes &a, const QPage &pg, RkPtr
         const uint4 v = rkp[r];
         rk[4 * r] = v.x; rk[4 * r + 1] = v.y; rk[4 * r + 2] = v.z; rk[4 * r + 3] = v.w;
     }
-    ctr_keystream_q4<NR, NB, STRIDE>(a, pg, rk, c0, ks);
+    ctr_keystream_q4<NR, NB, STRIDE, DEPTH>(a, pg, rk, c0, ks);
 }
 __device__ __forceinline__ uint4 ld_payload(const uint8_t *p) { return ld16(p); }
 #ifndef QPP_QUAD_NT
@@ -68,7 +92,32 @@ __device__ __forceinline__ void st_payload(uint8_t *p, uint4 v) {
     else st16(p, v);
 }
 template <int NR>  // (NR = 0: a launch over both sizes)
-constexpr int kQuadWG = NR == 14 ? QPP_QUAD_WG256 : QPP_QUAD_WG;
+constexpr int kQuadWG = NR == 10 ? QPP_QUAD_WG128 : NR == 14 ? QPP_QUAD_WG256 : QPP_QUAD_WG;
+// Pipeline depths by geometry: a 1024-thread instance has 128 VGPRs, not 168, and a fourth wave per SIMD to cover the
+// same LDS latency, so its GHASH product keeps fewer reads in flight (ghash.h DEPTH).  The 768-thread instances keep
+// QPP_GHASH_DEPTH / QPP_Q4_DEPTH and their code generation.
+#ifndef QPP_QUAD4_GHASH_DEPTH
+#define QPP_QUAD4_GHASH_DEPTH 6
+#endif
+#ifndef QPP_QUAD4_GHASH_ACC
+#define QPP_QUAD4_GHASH_ACC 1  // the running-sum product (ghash.h prod_acc): 16 registers fewer at the product's peak
+#endif
+#ifndef QPP_QUAD4_PEEL
+#define QPP_QUAD4_PEEL 1  // group 0 peeled off the group loop (quad_packet)
+#endif
+#ifndef QPP_QUAD4_Q4_DEPTH
+#define QPP_QUAD4_Q4_DEPTH QPP_Q4_DEPTH
+#endif
+template <int WG>
+struct QuadCfg {
+    static constexpr bool four = WG > 768;  // 4 waves per SIMD
+    static constexpr int gh_depth = four ? QPP_QUAD4_GHASH_DEPTH : QPP_GHASH_DEPTH;
+    static constexpr int q4_depth = four ? QPP_QUAD4_Q4_DEPTH : QPP_Q4_DEPTH;
+    static constexpr bool peel = four && QPP_QUAD4_PEEL;
+    using Gh = GhashT<true, gh_depth, four && QPP_QUAD4_GHASH_ACC>;
+};
+static_assert(kQuadWG<10> % 256 == 0 && kQuadWG<14> % 256 == 0 && kQuadWG<0> % 256 == 0 && kQuadWG<10> <= 1024,
+              "build_aes_tables_q4 needs whole 256-thread rows");
 // Counter blocks per lane in one group (a group = 4 QNB slots of the packet per quad).  4: 16 slots = 256 bytes of a
 // packet per group; fewer blocks per group hold fewer registers (the 1024-thread build, 4 waves per SIMD).
 #ifndef QPP_QUAD_NB
@@ -263,8 +312,8 @@ __device__ __forceinline__ qpp_pkt reload_desc(const qpp_pkt *descs, uint32_t i)
 
 // One packet per quad; s = lane % 4.  has = false: the quad has no packet (its lanes only keep the wave's loop shape).
 // Addresses are 32-bit offsets into the arena (SGPR base + VGPR offset).
-template <int NR, bool SEAL, bool HEAD>
-__device__ __forceinline__ void quad_packet(const QAes &aes, const GhashT<true> &gh, const DevKey *__restrict__ key,
+template <int NR, bool SEAL, bool HEAD, typename CFG>
+__device__ __forceinline__ void quad_packet(const QAes &aes, const typename CFG::Gh &gh, const DevKey *__restrict__ key,
                                             bool has, const qpp_pkt &d,
                                             const qpp_pkt *__restrict__ descs, uint32_t pkt_index,
                                             uint8_t *__restrict__ arena, uint8_t *masks, int8_t *status,
@@ -391,10 +440,14 @@ __device__ __forceinline__ void quad_packet(const QAes &aes, const GhashT<true> 
     };
 
     // one group: slots t = kQSG g + 4 k + s, k < NBG; slot t holds counter t + 1 and ciphertext block t - 1
-    auto group = [&](auto nbc, int g) __attribute__((always_inline)) {
-        constexpr int NBG = decltype(nbc)::value;
-        const bool head = NBG == kQNB && g == 0 && head_ok;  // uniform
-        const bool inner = NBG == kQNB && interior(g);  // uniform
+    // fc: whether this is group 0 -- -1: not known here (g says), 0 / 1: known (CFG::peel: group 0 is peeled off the
+    // group loop, so that what only group 0 needs -- the header bytes, the header-protection state, the J0 column's
+    // origin -- is not carried through the interior groups in registers)
+    auto group = [&](auto nbc, int g, auto fc) __attribute__((always_inline)) {
+        constexpr int NBG = decltype(nbc)::value, F = decltype(fc)::value;
+        const bool first = F < 0 ? g == 0 : F == 1;
+        const bool head = NBG == kQNB && first && head_ok;  // uniform
+        const bool inner = NBG == kQNB && !(F == 1) && interior(g);  // uniform
         const RkPtr rkp = round_keys();
         const int t0 = kQSG * g + (int)s;
         uint4 ks[NBG];
@@ -409,7 +462,7 @@ __device__ __forceinline__ void quad_packet(const QAes &aes, const GhashT<true> 
                 asm volatile("" : "+v"(m0), "+v"(m1), "+v"(m2));
                 pg.build(aes, rkp, m0, m1, m2, c0 >> 8);
             }
-            qkeystream<NR, NBG, 4>(aes, pg, rkp, c0, ks);
+            qkeystream<NR, NBG, 4, CFG::q4_depth>(aes, pg, rkp, c0, ks);
         } else {
             asm volatile("" : "+v"(m0), "+v"(m1), "+v"(m2));
             uint32_t rk[4 * (NR + 1)];
@@ -427,8 +480,13 @@ __device__ __forceinline__ void quad_packet(const QAes &aes, const GhashT<true> 
         // slower: 1.248 vs 1.152 ms seal, 8 VGPRs spilled, profiles/r04h_ab; loading this group's before the keystream
         // 4 % slower at 3 waves/SIMD (14 VGPRs spilled) and 7.5 % slower at 2 waves/SIMD (256 VGPRs, no spill); an L2
         // touch of the next group's lines 3.7 % slower: round 6, profiles/r06/head)
+        // (the general path's slot number laundered in the 128-VGPR instances: left alone, the compiler computed the
+        // per-lane byte offsets of a group's blocks and partial-block masks from s once per kernel, held them -- seven
+        // registers that only the last group of a packet reads -- and spilled them at the kernel's entry)
+        int tg = t0;
+        if constexpr (CFG::four) asm volatile("" : "+v"(tg));
         if (QPP_QUAD_PRIO) __builtin_amdgcn_s_setprio(QPP_QUAD_PRIO);
-        if (SEAL && g == 0 && hp_at0 && (flags & QPP_HP_APPLY) && s == 0) hb = hdr_load(at(pay - aad_len), aad_len - pn_len);
+        if (SEAL && first && hp_at0 && (flags & QPP_HP_APPLY) && s == 0) hb = hdr_load(at(pay - aad_len), aad_len - pn_len);
         if (head) {
             // slot 0 (lane 0, k = 0) reads the payload's first block instead of the bytes before it (never used)
             const uint32_t b = pay + 16 * (uint32_t)(t0 - 1);
@@ -444,7 +502,7 @@ __device__ __forceinline__ void quad_packet(const QAes &aes, const GhashT<true> 
         } else {
 #pragma unroll
             for (int k = 0; k < NBG; k++) {
-                const int j = t0 + 4 * k - 1;
+                const int j = tg + 4 * k - 1;
                 in[k] = ld_payload(at(pay + (j >= 0 && 16 * j <= (int)len ? 16 * (uint32_t)j : 0u)));
             }
         }
@@ -453,9 +511,9 @@ __device__ __forceinline__ void quad_packet(const QAes &aes, const GhashT<true> 
         for (int k = 0; k < NBG; k++) out[k] = in[k] ^ ks[k];
         if constexpr (SEAL) {
             // (QPP_QUAD_EK0C=0: E_K(J0), slot 0 of lane 0, kept whole in every lane until the tag is known)
-            if (g == 0 && !QPP_QUAD_EK0C) ek0 = ks[0];
+            if (first && !QPP_QUAD_EK0C) ek0 = ks[0];
         }
-        if (QPP_QUAD_EK0C && g == 0) {
+        if (QPP_QUAD_EK0C && first) {
             // slot 0 of group 0 is counter block 1 = J0 in lane 0: its column s to lane s (quad broadcasts of lane 0)
             const uint32_t c0w = qperm<kQuadBcast0>(ks[0].x), c1w = qperm<kQuadBcast0>(ks[0].y),
                            c2w = qperm<kQuadBcast0>(ks[0].z), c3w = qperm<kQuadBcast0>(ks[0].w);
@@ -497,7 +555,7 @@ __device__ __forceinline__ void quad_packet(const QAes &aes, const GhashT<true> 
             asm volatile("" : "+v"(rl));
 #pragma unroll
             for (int k = 0; k < NBG; k++) {
-                const int t = t0 + 4 * k, j = t - 1;
+                const int t = tg + 4 * k, j = t - 1;
                 const bool full = t >= 1 && j < nfull, part = rem && j == nfull, lenslot = has && t == m + 1;
                 if (full) st_payload(at(pay + 16 * (uint32_t)j), out[k]);
                 if (part) st_bytes(at(pay + 16 * (uint32_t)j), keep_bytes(out[k], rl), rl);
@@ -508,21 +566,40 @@ __device__ __forceinline__ void quad_packet(const QAes &aes, const GhashT<true> 
                 len_done = len_done || lenslot;
             }
         }
-        if (SEAL && g == 0 && !(QPP_QUAD_ABL & 4)) hp_early(out[0]);
+        if (SEAL && first && !(QPP_QUAD_ABL & 4)) hp_early(out[0]);
         if (QPP_QUAD_PRIO) __builtin_amdgcn_s_setprio(0);
     };
-    for (int g = 0; g + 1 < G; g++) group(std::integral_constant<int, kQNB>{}, g);
+    using Unknown = std::integral_constant<int, -1>;
+    using NotFirst = std::integral_constant<int, CFG::peel ? 0 : -1>;
+    using First = std::integral_constant<int, CFG::peel ? 1 : -1>;
+    if constexpr (CFG::peel) {
+        if (G > 1) group(std::integral_constant<int, kQNB>{}, 0, First{});
+        for (int g = 1; g + 1 < G; g++) group(std::integral_constant<int, kQNB>{}, g, NotFirst{});
+    } else {
+        for (int g = 0; g + 1 < G; g++) group(std::integral_constant<int, kQNB>{}, g, Unknown{});
+    }
     // open: the received tag's column s, loaded before the last group so that its round trip passes under that
     // group's work (it was loaded after the final product, its latency exposed once per packet)
     uint32_t want = 0;
     if (!SEAL && QPP_QUAD_TAGEARLY) __builtin_memcpy(&want, at(pay + len + 4 * s), 4);
-    if (G > 0) {  // the last group with as few counter blocks per lane as its longest packet needs
-        // (small packets: a 300-B packet's second group needs 1 block per lane, not 3)
-        if (tail_slots <= 4) group(std::integral_constant<int, 1>{}, G - 1);
-        else if (kQNB == 2 || tail_slots <= 8) group(std::integral_constant<int, 2>{}, G - 1);
-        else if (kQNB == 3 || tail_slots <= 12) group(std::integral_constant<int, kQNB < 3 ? kQNB : 3>{}, G - 1);
-        else group(std::integral_constant<int, kQNB>{}, G - 1);
+    // the last group with as few counter blocks per lane as its longest packet needs
+    // (small packets: a 300-B packet's second group needs 1 block per lane, not 3)
+    // (a macro, not a lambda around group: the nested closure changed the 768-thread instances' register allocation)
+#define QPP_LAST_GROUP(FC)                                                                                      \
+    do {                                                                                                        \
+        if (tail_slots <= 4) group(std::integral_constant<int, 1>{}, G - 1, FC{});                              \
+        else if (kQNB == 2 || tail_slots <= 8) group(std::integral_constant<int, 2>{}, G - 1, FC{});            \
+        else if (kQNB == 3 || tail_slots <= 12)                                                                 \
+            group(std::integral_constant<int, kQNB < 3 ? kQNB : 3>{}, G - 1, FC{});                             \
+        else group(std::integral_constant<int, kQNB>{}, G - 1, FC{});                                           \
+    } while (0)
+    if constexpr (CFG::peel) {
+        if (G == 1) QPP_LAST_GROUP(First);
+        else if (G > 1) QPP_LAST_GROUP(NotFirst);
+    } else {
+        if (G > 0) QPP_LAST_GROUP(Unknown);
     }
+#undef QPP_LAST_GROUP
     if (!len_done && (((m + 1) & 3) == (int)s)) w = gh.mulx(w, lenblk());
     // this lane's chain times H^e, e = (m + 2) - its last slot; then the quad's sum
     const int t_last = (m + 1) - (((m + 1) - (int)s) & 3);
@@ -632,7 +709,8 @@ __device__ __forceinline__ void quad_slices(const DevKey *__restrict__ keys, con
         if (work[mid].begin <= lo) i = mid; else j = mid;
     }
     const QAes aes = make_qaes();
-    const GhashT<true> gh = GhashT<true>::make();
+    using CFG = QuadCfg<WG>;
+    const typename CFG::Gh gh = CFG::Gh::make();
     const uint32_t s = threadIdx.x & 3u, q = threadIdx.x >> 2;
     build_qaes();  // once: the segments' table builds from a pow slot leave them alone (the first barrier below orders it)
 #if QPP_QUAD_TRACE
@@ -667,7 +745,7 @@ __device__ __forceinline__ void quad_slices(const DevKey *__restrict__ keys, con
                 if (status && s == 0) status[pi] = QPP_INTERNAL_ERROR;
                 has = false;
             }
-            quad_packet<NR, SEAL, HEAD>(aes, gh, key, has, d, descs, pi, arena, masks, status, flags, s);
+            quad_packet<NR, SEAL, HEAD, CFG>(aes, gh, key, has, d, descs, pi, arena, masks, status, flags, s);
         }
         lo = end;
     }
@@ -776,9 +854,10 @@ __device__ __forceinline__ uint32_t rx_class(uint4 kw, bool chacha) {
 }
 
 // AES: 10 or 14 when the live AES packet keys are all of one size (that instance alone: no registers spent on the
-// other), 0 for both sizes in one launch (the launch's workgroup size: kQuadWG<10>, or kQuadWG<14> for 14 alone)
+// other), 0 for both sizes in one launch (the launch's workgroup size: kQuadWG<0>, or kQuadWG<14> for 14 alone -- not
+// the AES-128 seal / open pair's own geometry: the grid barriers and phases A-C were measured at 768 threads)
 template <int AES>
-constexpr int kRxWG = AES == 14 ? kQuadWG<14> : kQuadWG<10>;
+constexpr int kRxWG = AES == 14 ? kQuadWG<14> : kQuadWG<0>;
 template <int AES>
 __global__ __launch_bounds__(kRxWG<AES>) void aes_gcm_quad_rx_kernel(const DevKey *__restrict__ keys,
                                                                  uint32_t key_cap, const qpp_rx_pkt *__restrict__ rx,
